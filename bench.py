@@ -10,13 +10,18 @@ Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line
                                                                  ranks itself, one per GPU, and relays rank 0's line)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-The JSON line also carries
+A plain run sets up, warms up (3 priming + W + SETTLE_STEPS untimed steps), times ONE region of exactly K steps and prints
+the headline line (metric, value, unit, higher_is_better, dtype, ms_per_step, config).  --dump-outputs DIR also writes what the last timed step returned
+(loss, logits) and a fixed seeded sample of the parameters it updated as DIR/<name>.npy.  With --full the JSON line
+also carries
   roofline      dominant kernel (the frozen stem's composed 5x5 conv): executed FLOPs / HIP-event launch time vs the dense bf16 MFMA peak
   cpu_baseline  the CPU oracle (a port of the reference) on this host's cores: B=8 clips, 1 warm-up + 3 timed steps
   parity        bf16 benchmark precision vs the exact-f32 parity precision on the SAME weights and batches at this very
                 workload: max logits error relative to max |logit|, argmax agreement, loss error, fp32-mode clips/s
-  repeats       the timed K-step region is run `--repeats` times (default 3); `value` is the MEDIAN region
+  repeats       the timed K-step region is run `--repeats` times (default 3 with --full, 1 without); `value` is the MEDIAN region
   comm          (N > 1) ranks, all-reduce payload / time, and the exposed (non-overlapped) communication per step
+and the stem-alone figures, the idle-queue enqueue cost, the inference path's region (`eval_mode`) and the other storage
+precisions' own lines (`bf16_mode`, `fp16_mode`).
 """
 import argparse
 import json
@@ -68,6 +73,10 @@ def trunk_flops_per_frame(S, C_in, C, blocks, at):
 
 
 COMPOSED_STEM = [True]     # set by build(): whether the frozen stem evaluates conv11 . conv12 as one composed 5x5 conv
+# Untimed steps a plain run adds right before its one timed region: on MI355X the first ~20 steps after the warm-up's gc.collect() ran
+# ~2 % slower than the ones after them (the launch thread, 8 of the step's 8.7 ms, is slower for them); --full's median of three
+# regions leaves that first region out instead.
+SETTLE_STEPS = 20
 
 
 def build(args, device):
@@ -254,7 +263,7 @@ def fp16_leg(args, precision="fp16"):
     backward) measured on the same workload in a CHILD process — one 16-bit storage format per process — after this
     process's own measurement: throughput of a short run and its parity block against the exact-f32 precision."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--precision", precision, "--no-cpu-baseline", "--no-fp16-leg", "--no-eval-leg", "--no-robustness",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--precision", precision, "--no-cpu-baseline", "--no-fp16-leg", "--no-eval-leg", "--no-robustness",
            "--repeats", "1",
            "--steps", str(args.steps), "--warmup", str(args.warmup), "--batch", str(args.batch), "--frames", str(args.frames),
            "--height", str(args.height), "--width", str(args.width), "--blocks", str(args.blocks), "--channels", str(args.channels)]
@@ -290,6 +299,25 @@ def fp16_leg(args, precision="fp16"):
         return {"error": "%s leg exceeded 420 s" % precision}
 
 
+DUMP_PARAM_SAMPLE = 1 << 20      # parameters written by --dump-outputs (4 MB of float32; the metric's model has ~18 M)
+
+
+def dump_outputs(out_dir, loss, logits, flat=None):
+    """--dump-outputs: what the last timed step handed its caller — the loss (float64, shape ()) and the logits (float32, rows in
+    the order the step returns them) — and, for a training step, the parameters it updated: a fixed seeded sample of
+    DUMP_PARAM_SAMPLE entries of the flat fp32 parameter buffer (all of it when smaller), in index order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": np.asarray(float(loss), dtype=np.float64),
+              "logits": logits.detach().float().cpu().numpy()}
+    if flat is not None:
+        n = flat.numel()
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_PARAM_SAMPLE].sort().values
+        arrays["params_sample"] = flat.detach()[idx.to(flat.device)].float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def bench_cnn3d(args):
     """BASELINE config 2 (`--model v_only_cnn3d`): VideoOnlyCNN3D on 1 MI355X, synthetic 16x3x112x112 clips, bs = 32 unless --batch is
     given explicitly, forward + backward + fused clip+Adam over the flat parameter buffer; one JSON line in the same schema.
@@ -311,20 +339,23 @@ def bench_cnn3d(args):
 
     def step(i):
         x, y = batches[i % len(batches)]
-        loss = ops.cross_entropy(model(x), y, reduction="sum")
+        logits = model(x)
+        loss = ops.cross_entropy(logits, y, reduction="sum")
         loss.backward()
         fp.clip_adam_step(1e-4, 1e30)
-        return loss
-    for i in range(args.warmup):
+        return loss, logits.detach()
+    for i in range(args.warmup + (0 if args.full else SETTLE_STEPS)):
         step(i)
     regions = []
     for _ in range(args.repeats):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            loss = step(i)
+            loss, logits = step(i)
         torch.cuda.synchronize()
         regions.append(time.perf_counter() - t0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, logits, fp.flat)
     dt = sorted(regions)[len(regions) // 2]
     conv = 3 * B * (2.0 * D * H * W * 3 * 64 * 27 + 2.0 * D * (H // 2) * (W // 2) * 64 * 128 * 27
                     + 2.0 * (D // 4) * (H // 8) * (W // 8) * 128 * 128 * 27)
@@ -832,8 +863,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=3, help="the timed K-step region is run this many times back to back; "
-                    "the reported value / ms_per_step are the MEDIAN region's, all regions are listed in `repeats`")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed K-step region is run this many times back to back; "
+                    "the reported value / ms_per_step are the MEDIAN region's, all regions are listed in `repeats` "
+                    "(default 3 with --full, else 1)")
+    ap.add_argument("--full", action="store_true", help="measure and check everything beside the headline as well: CPU baseline, "
+                    "parity against the exact-f32 precision and the CPU oracle (incl. the robustness sweep), the bf16 / fp16 legs, "
+                    "roofline and stem-alone figures, the idle-queue enqueue cost, the inference path's region, (N > 1) the comm "
+                    "block; the --no-* options below switch parts of it off.  Without it a run sets up, warms up, times the "
+                    "--steps steps, writes --dump-outputs and prints the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the last one returned "
+                    "(loss.npy float64, logits.npy float32) and a fixed seeded sample of the parameters it updated "
+                    "(params_sample.npy float32; training only) to DIR")
     ap.add_argument("--precision", default="fp16h", choices=["bf16", "fp16", "fp16h", "fp32"],
                     help="fp16h (default, the headline; also the default of every model constructor and CLI): the TOLERANCE-COMPLIANT precision — "
                          "fp16 storage and fp16 MFMA products with fp32 accumulation, stem weights second-order rounded on calibration frames, "
@@ -885,6 +925,8 @@ def main():
     args = ap.parse_args()
     if args.batch is None:
         args.batch = 32 if args.model == "v_only_cnn3d" else 8
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
     if args.cpu_baseline_only:
         cpu_baseline_child(args)
         return
@@ -916,7 +958,7 @@ def main():
     if world != args.gpus:
         raise SystemExit("--gpus %d does not match WORLD_SIZE %d" % (args.gpus, world))
     cpu_leg, oracle_dump = None, None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         import tempfile
         fwd = [a for a in sys.argv[1:] if a not in ("--no-cpu-baseline",)]
         if args.model == "film_attn_pt" and not args.no_parity:
@@ -1003,12 +1045,12 @@ def main():
         gc.disable()          # the launch thread must not stall in the cyclic collector mid-step
 
     def timed_region():
-        """EXACTLY --steps steps between barrier + synchronize on both sides; max over ranks."""
-        stem.timing = []          # (start, end) HIP events around every stem-tagged igemm launch
+        """EXACTLY --steps steps between barrier + synchronize on both sides; max over ranks.  Returns the last step's output."""
+        stem.timing = [] if args.full else None       # (--full: start, end HIP events around every stem-tagged igemm launch)
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            loss, _ = run_step()
+            out = run_step()
         t_enq = time.perf_counter() - t0      # host time to ENQUEUE the K steps (launch-thread cost, no device wait)
         barrier()
         dt = time.perf_counter() - t0
@@ -1018,7 +1060,7 @@ def main():
             t = torch.tensor([dt], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        return dt, t_enq, ev, loss
+        return dt, t_enq, ev, out
 
     if args.mode == "eval":
         # inference (val_epoch / test, eval/q_and_v_eval.py:159-224, eval/q_and_v_test.py:64-142): the SAME timed-region protocol
@@ -1032,24 +1074,31 @@ def main():
             return trainer.eval_step(*b, next_clip=bn[0], next_v_lens_cpu=bn[2])[:2]
         for _ in range(3 + args.warmup):
             run_step()
+    if not args.full:         # one timed region: start it in the steady state
+        for _ in range(SETTLE_STEPS):
+            run_step()
     regions = [timed_region() for _ in range(max(args.repeats, 1))]
     order = sorted(range(len(regions)), key=lambda i: regions[i][0])
-    dt, t_enqueue, events, loss = regions[order[len(order) // 2]]          # the MEDIAN region is the reported one
+    dt, t_enqueue, events, (loss, _) = regions[order[len(order) // 2]]     # the MEDIAN region is the reported one
+    if args.dump_outputs and rank == 0:         # the last timed step's outputs, before any later step overwrites the parameters
+        dump_outputs(args.dump_outputs, *regions[-1][3][:2], flat=trainer.fp.flat if args.mode == "train" else None)
     # Host cost of ONE step's enqueue on an IDLE queue (the in-region figure includes back-pressure — a launch
     # thread that is ahead of the GPU blocks in the runtime once the hardware queues are full, which looks like launch cost):
     # synchronize, enqueue one step, stop the clock before waiting for it; median of five.  Not part of the timed region.
-    idle = []
-    for _ in range(5):
+    t_enqueue_idle = None
+    if args.full:
+        idle = []
+        for _ in range(5):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run_step()
+            idle.append(time.perf_counter() - t0)
         torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        run_step()
-        idle.append(time.perf_counter() - t0)
-    torch.cuda.synchronize()
-    t_enqueue_idle = sorted(idle)[len(idle) // 2]
+        t_enqueue_idle = sorted(idle)[len(idle) // 2]
 
     # the inference path's throughput next to the training headline (same protocol, same resident minibatches, one region)
     eval_mode = None
-    if args.mode == "train" and world == 1 and not args.h2d and args.model != "mac" and not args.no_eval_leg:
+    if args.full and args.mode == "train" and world == 1 and not args.h2d and args.model != "mac" and not args.no_eval_leg:
         train_step = run_step
 
         def run_step():       # noqa: F811
@@ -1069,7 +1118,7 @@ def main():
     # (N > 1) what the gradient all-reduce costs: the flat buffer's all-reduce alone, and the step WITHOUT collectives
     # (replicas diverge from here on: after the measurement) -> exposed communication per step
     comm = None
-    if world > 1:
+    if args.full and world > 1:
         g = trainer.fp.grad
         for _ in range(2):
             dist.all_reduce(g)
@@ -1099,8 +1148,8 @@ def main():
     gc.enable()
     # north-star side metric, outside the timed region: the frozen stem ALONE on the chip (all B*T frames,
     # conv1_1 .. conv32), as a fraction of the dense bf16 MFMA peak
-    stem_ms = None
-    if rank == 0:
+    stem_ms, alone_events = None, []
+    if args.full and rank == 0:
         dev_clip = batch[0].to(device)
         lay = trainer.extract_features(dev_clip, batch[2])[0].layout
         torch.cuda.synchronize()
@@ -1119,7 +1168,7 @@ def main():
         alone_events, stem.timing = stem.timing, None
     parity = None
     # (single-GPU runs only: at N > 1 the other ranks would sit in the barrier below for the minute this takes)
-    if world == 1 and not args.no_parity and args.model != "mac" and args.precision in ("bf16", "fp16", "fp16h"):
+    if args.full and world == 1 and not args.no_parity and args.model != "mac" and args.precision in ("bf16", "fp16", "fp16h"):
         loss = loss.clone()
         del trainer, model, stem
         torch.cuda.empty_cache()
@@ -1139,7 +1188,7 @@ def main():
         # HIP events around every launch of the frozen stem's C_out = 512 layers, grouped by the kernel that served them: the
         # DOMINANT kernel (most time in the timed region) is the roofline's subject, the other is listed beside it
         by_kernel = {}
-        for ev in events:
+        for ev in events or ():          # (recorded with --full only)
             k = ev[3] if len(ev) > 3 else "conv_igemm_kernel"
             by_kernel.setdefault(k, []).append((ev[0].elapsed_time(ev[1]), ev[2]))
         kstats = {}
@@ -1213,38 +1262,40 @@ def main():
                        "final_loss": round(float(loss), 4), "minibatches_rotated": NB, "inputs": ("pinned host memory, H2D every step" if args.h2d else "resident in HBM") +
                                  (", raw uint8 pixels (k / 255 formed on the device)" if args.clip_dtype == "u8" else ""),
                        "host_enqueue_ms_per_step": round(t_enqueue / args.steps * 1e3, 3),
+                       "stem_formulation": ("conv11.conv12 composed into one 5x5 conv + exact border correction"
+                                            if composed else "layer by layer")},
+        }
+        if args.full:
+            out["config"].update({
                        # the same step enqueued on an IDLE queue (no back-pressure from a busy GPU): the launch thread's own cost
                        "host_enqueue_idle_queue_ms_per_step": round(t_enqueue_idle * 1e3, 3),
                        "stem_alone_ms": round(stem_ms, 3),
                        # whole frozen stem alone on the chip: EXECUTED FLOPs / time / peak (hardware utilisation) and the
                        # same with the reference formulation's algorithmic FLOPs (37.167 GF/frame at 224x224)
-                       "stem_formulation": ("conv11.conv12 composed into one 5x5 conv + exact border correction"
-                                            if composed else "layer by layer"),
                        "stem_alone_mfma_util": round(n_frames * stem_executed_flops_per_frame(H, W, composed)
                                                      / (stem_ms * 1e-3) / 1e12 / peak, 4),
                        "stem_alone_mfma_util_algorithmic": round(n_frames * stem_flops_per_frame(H, W) / (stem_ms * 1e-3)
-                                                                 / 1e12 / peak, 4)},
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4), "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": {"conv_igemm_kernel": "conv_igemm_kernel<%s,256,256,2,4,TAG=1> (frozen-stem implicit GEMM on v_mfma_f32_16x16x32: "
-                                                         "the composed 5x5 conv11.conv12 and any C_out=512 layer the patch-stationary "
-                                                         "kernel does not serve; FLOPs = those its launches execute)"
-                                                         % ("bf16" if args.precision == "bf16" else "f16"),
-                                    "conv_ps_kernel<28,5x5>": "conv_ps_kernel<28,2,TAG=1> (frozen-stem patch-stationary conv on v_mfma_f32_16x16x32, 5x5 "
-                                                              "instantiation: the composed conv11.conv12 on 8 x 28-pixel 2-D tiles, border correction, ReLU "
-                                                              "floor and 2x2 pool fused; FLOPs = those its launches execute)",
-                                    "conv_ps_kernel<28>": "conv_ps_kernel<28,1,TAG=1> (patch-stationary 3x3 conv, 4 waves x 512 registers: conv21, "
-                                                          "conv22 on 28x28 maps; FLOPs = those its launches execute)",
-                                    "conv_ps_kernel<14>": "conv_ps_kernel<14,1,TAG=1> (patch-stationary 3x3 conv: conv31, conv32 on 14x14 maps)"}.get(dom, dom),
-                         "measured": "HIP events around every launch of this kernel in the timed region, while the trunk stream "
-                                     "co-runs on the same chip (see stem_alone_* for the kernel with the chip to itself)",
-                         # the same kernel's launches with no other stream on the chip (stem-alone pass after the timed region):
-                         # the timed-region figure above is lower because the previous step's trunk kernels share the CUs
-                         "chip_to_itself": dstat.get("chip_to_itself"),
-                         "other_stem_kernels": {k: v for k, v in kstats.items() if k != dom},
-                         "launches_per_step": launches_per_step, "avg_launch_ms": round(avg_ms, 4),
-                         "gflop_per_launch": round(flops_per_launch / 1e9, 1)},
-        }
+                                                                 / 1e12 / peak, 4)})
+            out["roofline"] = {"bound": "mfma", "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
+                               "frac": round(achieved / peak, 4), "traffic": traffic, "traffic_source": traffic_src,
+                               "kernel": {"conv_igemm_kernel": "conv_igemm_kernel<%s,256,256,2,4,TAG=1> (frozen-stem implicit GEMM on v_mfma_f32_16x16x32: "
+                                                               "the composed 5x5 conv11.conv12 and any C_out=512 layer the patch-stationary "
+                                                               "kernel does not serve; FLOPs = those its launches execute)"
+                                                               % ("bf16" if args.precision == "bf16" else "f16"),
+                                          "conv_ps_kernel<28,5x5>": "conv_ps_kernel<28,2,TAG=1> (frozen-stem patch-stationary conv on v_mfma_f32_16x16x32, 5x5 "
+                                                                    "instantiation: the composed conv11.conv12 on 8 x 28-pixel 2-D tiles, border correction, ReLU "
+                                                                    "floor and 2x2 pool fused; FLOPs = those its launches execute)",
+                                          "conv_ps_kernel<28>": "conv_ps_kernel<28,1,TAG=1> (patch-stationary 3x3 conv, 4 waves x 512 registers: conv21, "
+                                                                "conv22 on 28x28 maps; FLOPs = those its launches execute)",
+                                          "conv_ps_kernel<14>": "conv_ps_kernel<14,1,TAG=1> (patch-stationary 3x3 conv: conv31, conv32 on 14x14 maps)"}.get(dom, dom),
+                               "measured": "HIP events around every launch of this kernel in the timed region, while the trunk stream "
+                                           "co-runs on the same chip (see stem_alone_* for the kernel with the chip to itself)",
+                               # the same kernel's launches with no other stream on the chip (stem-alone pass after the timed region):
+                               # the timed-region figure above is lower because the previous step's trunk kernels share the CUs
+                               "chip_to_itself": dstat.get("chip_to_itself"),
+                               "other_stem_kernels": {k: v for k, v in kstats.items() if k != dom},
+                               "launches_per_step": launches_per_step, "avg_launch_ms": round(avg_ms, 4),
+                               "gflop_per_launch": round(flops_per_launch / 1e9, 1)}
         if args.mode == "eval":
             out["metric"] = METRIC.replace("fwd+bwd", "forward only (inference: val_epoch / test)")
             out["config"]["workload"] = out["config"]["workload"].replace("training step", "INFERENCE step (eval mode, no backward / optimizer)")
@@ -1254,7 +1305,7 @@ def main():
             out["comm"] = comm
         if parity is not None:
             out["parity"] = parity
-        if world == 1 and args.precision == "fp16h" and not args.no_fp16_leg and not args.no_parity and args.model == "film_attn_pt":
+        if args.full and world == 1 and args.precision == "fp16h" and not args.no_fp16_leg and not args.no_parity and args.model == "film_attn_pt":
             # the other storage precisions' own lines (child processes: one 16-bit format per process) — NOT tolerance-compliant:
             # bf16 is BASELINE.json's storage dtype (logits ~7e-3 of exact fp32), fp16 the plain fp16 storage (0.6-1.0e-3 rms by seed)
             out["bf16_mode"] = fp16_leg(args, "bf16")

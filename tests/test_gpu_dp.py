@@ -107,7 +107,7 @@ SMALL = ["--steps", "2", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline",
 def test_bench_gpus2_spawns_its_own_ranks_single_device_gloo():
     """`bench.py --gpus 2` with no launcher: the parent starts both ranks itself (here on ONE GPU over gloo — the test
     hook for 1-GPU boxes), rank 0 prints the single JSON line with n_gpus = 2 and the comm block."""
-    out = _run_bench({"VNQA_DIST_BACKEND": "gloo", "VNQA_SINGLE_DEVICE": "1"}, ["--gpus", "2"] + SMALL)
+    out = _run_bench({"VNQA_DIST_BACKEND": "gloo", "VNQA_SINGLE_DEVICE": "1"}, ["--gpus", "2", "--full"] + SMALL)
     assert out["n_gpus"] == 2 and out["config"]["global_batch"] == 4 and out["config"]["parallelism"] == "dp2"
     c = out["comm"]
     assert c["ranks"] == 2 and c["backend"] == "gloo" and c["allreduce_alone_ms"] > 0
@@ -120,9 +120,9 @@ def test_bench_gpus2_rccl_two_gpus():
     """Two ranks on two MI355X over RCCL through the self-spawning entry point; also A/Bs the persistent conv kernels'
     CU reservation (VNQA_STEM_RESERVE_CUS: a CU-masked stem stream, the persistent conv kernels sized for it), which exists for exactly
     this co-scheduling with RCCL's kernels."""
-    base = _run_bench({}, ["--gpus", "2", "--steps", "5", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline", "--no-parity"])
+    base = _run_bench({}, ["--gpus", "2", "--full", "--steps", "5", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline", "--no-parity"])
     assert base["n_gpus"] == 2 and base["comm"]["backend"] == "rccl" and base["comm"]["ranks"] == 2
-    resv = _run_bench({"VNQA_STEM_RESERVE_CUS": "32"}, ["--gpus", "2", "--steps", "5", "--warmup", "2", "--repeats", "1",
+    resv = _run_bench({"VNQA_STEM_RESERVE_CUS": "32"}, ["--gpus", "2", "--full", "--steps", "5", "--warmup", "2", "--repeats", "1",
                                                        "--no-cpu-baseline", "--no-parity"])
     print("dp2 clips/s: reserve 0 -> %.1f, reserve 32 -> %.1f; exposed comm %.3f / %.3f ms"
           % (base["value"], resv["value"], base["comm"]["exposed_comm_ms_per_step"], resv["comm"]["exposed_comm_ms_per_step"]))

@@ -5,7 +5,7 @@
 A=$1; B=$2; R=${3:-3}; shift 3
 for i in $(seq $R); do
   for L in $A $B; do
-    V=$(VNQA_LIB=$PWD/videonavqa_amd/lib/$L timeout 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline "$@" 2>/dev/null | tail -1 | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["config"]["stem_alone_ms"])')
+    V=$(VNQA_LIB=$PWD/videonavqa_amd/lib/$L timeout 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline "$@" 2>/dev/null | tail -1 | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["config"]["stem_alone_ms"])')
     echo "$L $V"
   done
 done

@@ -7,7 +7,7 @@ for i in 1 2; do for v in $V; do
   echo "PS,XCD=$v $(VNQA_COMPOSED_PS=${v%,*} VNQA_COMPOSED_PS_XCD=${v#*,} timeout 120 python3 tools/stem_only.py --iters 20 2>/dev/null < /dev/null | tail -1)"
 done; done | tee $O/stem_ab.txt
 for i in 1 2; do for v in $V; do
-  VNQA_COMPOSED_PS=${v%,*} VNQA_COMPOSED_PS_XCD=${v#*,} timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-parity --no-fp16-leg --no-eval-leg --no-robustness 2>/dev/null < /dev/null | tail -1 | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["config"].get("stem_alone_ms"))' | sed "s/^/PS,XCD=$v /"
+  VNQA_COMPOSED_PS=${v%,*} VNQA_COMPOSED_PS_XCD=${v#*,} timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-parity --no-fp16-leg --no-eval-leg --no-robustness 2>/dev/null < /dev/null | tail -1 | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["config"].get("stem_alone_ms"))' | sed "s/^/PS,XCD=$v /"
 done; done | tee $O/bench_ab.txt
 cd /tmp && export TMPDIR=/tmp
 export VNQA_COMPOSED_PS=1

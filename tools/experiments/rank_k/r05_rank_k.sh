@@ -24,7 +24,7 @@ for seed in 0 1 2 3; do
 done
 echo "smooth: $(timeout 600 python tools/error_budget.py --precision fp16h --data smooth 2>/dev/null | tail -1)" >> $O
 q() { tail -1 | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print("%.1f clips/s  %.3f ms/step  stem alone %.3f" % (d["value"], d["ms_per_step"], d["config"]["stem_alone_ms"]))'; }
-A="--no-cpu-baseline --no-fp16-leg --no-eval-leg --no-parity --repeats 3"
+A="--full --no-cpu-baseline --no-fp16-leg --no-eval-leg --no-parity --repeats 3"
 for r in 1 2 3; do
   echo "fp16h: $(python bench.py $A 2>/dev/null | q)   bf16: $(python bench.py $A --precision bf16 2>/dev/null | q)" >> $O
 done

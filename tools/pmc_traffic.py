@@ -35,7 +35,7 @@ def per_dispatch(d, counter, pat):
 
 
 res = {"command": sys.argv[3] if len(sys.argv) > 3 else
-       "rocprofv3 --kernel-trace --pmc {FETCH_SIZE|WRITE_SIZE} --output-format csv -- python3 bench.py --steps 3 --warmup 1 "
+       "rocprofv3 --kernel-trace --pmc {FETCH_SIZE|WRITE_SIZE} --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 "
        "--repeats 1 --no-parity --no-cpu-baseline --no-overlap (two separate passes)",
        "correction": "gfx950: FETCH_SIZE counts 64 B per 128-B request for wide coalesced reads -> doubled (MI355X_MICROARCH.md, HBM); "
                      "WRITE_SIZE exact; both in KiB", "kernels": {}}

@@ -4,6 +4,6 @@
 R=$PWD; export PYTHONPATH=$R; PREC=${PREC:-fp16h}
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/ps
 TR="--kernel-trace"; if [ "$MEMCPY" = "1" ]; then TR="--kernel-trace --memory-copy-trace"; fi
-rocprofv3 $TR -d /tmp/ps -- python3 $R/bench.py --precision $PREC --steps 6 --warmup 3 --repeats 1 --no-parity --no-cpu-baseline --no-eval-leg --no-fp16-leg "$@" > /tmp/ps.out 2> /tmp/ps.err
+rocprofv3 $TR -d /tmp/ps -- python3 $R/bench.py --full --precision $PREC --steps 6 --warmup 3 --repeats 1 --no-parity --no-cpu-baseline --no-eval-leg --no-fp16-leg "$@" > /tmp/ps.out 2> /tmp/ps.err
 cd $R
 python3 tools/step_streams.py /tmp/ps 2 ${NSTEPS:-1}

@@ -27,7 +27,7 @@ def main():
     ap.add_argument("--bench")
     ap.add_argument("--bench-nooverlap")
     ap.add_argument("--profiled")
-    ap.add_argument("--command", default="python3 bench.py --steps 20 --warmup 5 --repeats 1 --no-parity --no-cpu-baseline")
+    ap.add_argument("--command", default="python3 bench.py --full --steps 20 --warmup 5 --repeats 1 --no-parity --no-cpu-baseline")
     a = ap.parse_args()
     if a.trace_dir.endswith(".csv"):      # re-summarise an earlier run from its committed CSV (same columns as written below)
         with open(a.trace_dir) as f:

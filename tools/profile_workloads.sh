@@ -8,14 +8,14 @@ OUT=$ROOT/gpurun_out/${TAG}_other_workloads.md
 mkdir -p $ROOT/gpurun_out
 echo "# Round $R — other workloads: bench line + rocprofv3 kernel trace (top kernels by GPU time)" > $OUT
 echo "" >> $OUT
-echo "Each section: \`python3 bench.py <args> --steps 10 --warmup 3 --repeats 1 --no-parity --no-cpu-baseline --no-fp16-leg\` under" >> $OUT
+echo "Each section: \`python3 bench.py <args> --full --steps 10 --warmup 3 --repeats 1 --no-parity --no-cpu-baseline --no-fp16-leg\` under" >> $OUT
 echo "\`rocprofv3 --kernel-trace --stats\`.  Under the profiler the launch thread becomes the bound (host enqueue = the step time), so the clips/s here are 5-30 % below the un-profiled ladder in README.md; the per-kernel durations are what this file is for.  ms/step = total kernel time / 16 steps" >> $OUT
 echo "(3 priming + 3 warm-up + 10 timed); the stem-alone passes bench.py runs after the timed region inflate the stem rows by ≈1.3×." >> $OUT
 cd /tmp && export TMPDIR=/tmp
 run() {
   name=$1; shift
   rm -rf /tmp/pw
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pw -- python3 $ROOT/bench.py "$@" --steps 10 --warmup 3 --repeats 1 --no-parity --no-cpu-baseline --no-fp16-leg > /tmp/pw_bench.json 2> /tmp/pw.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pw -- python3 $ROOT/bench.py "$@" --full --steps 10 --warmup 3 --repeats 1 --no-parity --no-cpu-baseline --no-fp16-leg > /tmp/pw_bench.json 2> /tmp/pw.err
   f=$(find /tmp/pw -name '*kernel_stats.csv' | head -1)
   python3 - "$name" "$f" /tmp/pw_bench.json "$*" >> $OUT <<'EOF'
 import csv, json, sys
